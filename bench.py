@@ -24,6 +24,14 @@ itself on device memory, with the ranks the process group saw -- at N=1 a one-ra
 after the timed region (the headline stays the plain single-GPU step); `--force-collective` puts it INSIDE the timed
 step at N=1 as well.
 
+A plain run (`python bench.py --gpus N --steps K --warmup W`) does only what the headline needs: it sets up, warms up,
+times the K steps, writes what the last timed step computed if `--dump-outputs DIR` is given (`DIR/returns.npy`: the
+fp32 episode returns the kernel wrote, `DIR/costs.npy`: the float64 per-candidate costs the step handed back), and prints
+the line (the contract's keys, `config`, `generation_cost_checksum`).  Everything described below -- the parity
+samples, the extra blocks, the CPU baselines, the CMA-ES generation wall-clock, `roofline` with its own kernel timings,
+the collective timed by itself, `predicted_strong_scaling` and the side file -- runs only with `--full`
+(`--no-extras`, `--no-parity`, `--no-cpu-baseline` trim a `--full` run).
+
 `python bench.py --gpus N` starts its N ranks itself (a torch.distributed.run child, spawned before
 anything touches the GPU) unless it already runs under a launcher (WORLD_SIZE set); the world size
 must equal --gpus or the run fails.
@@ -289,7 +297,8 @@ def compact_line(out, detail_path):
     cfg = out["config"]
     line["config"] = {"workload": cfg["workload"], "episodes_per_generation": cfg["episodes_per_generation"],
                       "episodes_per_gpu": cfg["episodes_per_gpu"], "sharding": cfg["sharding"]}
-    line["roofline"] = compact_roofline(out["roofline"])
+    if "roofline" in out:
+        line["roofline"] = compact_roofline(out["roofline"])
     cb = out.get("cpu_baseline")
     if cb:
         line["cpu_baseline"] = {"value": cb["value"], "unit": cb["unit"], "cores": cb["cores"], "kind": cb["kind"],
@@ -315,7 +324,8 @@ def compact_line(out, detail_path):
             "measured_on": "every rank's block timed on ONE GPU + the one-rank all-gather; NOT an N-GPU run",
             **{c: [[r["n_gpus"], _sig(r["generation_ms"], 4), _sig(r["speedup"], 3), _sig(r["efficiency"], 3)]
                    for r in t["rows"]] for c, t in pss["configs"].items()}}
-    line["detail"] = detail_path
+    if detail_path is not False:                              # (a plain run writes no side file)
+        line["detail"] = detail_path
     return line
 
 
@@ -335,12 +345,26 @@ def write_detail(out):
     return None
 
 
-def print_line(out, line_out):
-    line = compact_line(out, write_detail(out))
+def print_line(out, line_out, detail=True):
+    line = compact_line(out, write_detail(out) if detail else False)
     text = json.dumps(line, separators=(",", ":"))
     if len(text) >= LINE_CAP:
         raise SystemExit(f"bench.py: the line is {len(text)} bytes (cap {LINE_CAP}); move keys to {DETAIL_NAME}")
     print(text, file=line_out, flush=True)
+
+
+DUMP_CAP = 64 << 20
+
+
+def dump_outputs(dirname, arrays):
+    """--dump-outputs: what the last timed step computed, one DIR/<name>.npy per array (float32 / float64).  The inputs
+    are seeded, so two builds run with the same arguments can be compared output for output."""
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_CAP:
+        raise SystemExit(f"bench.py: the outputs are {total} bytes (cap {DUMP_CAP})")
+    os.makedirs(dirname, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(dirname, f"{name}.npy"), a)
 
 
 def spawn_ranks(args):
@@ -376,7 +400,8 @@ def plumbing_check(args, world, rank, line_out):
         dist.destroy_process_group()
     if rank == 0:
         print(json.dumps({"plumbing": True, "n_gpus": world, "torch": torch.__version__, "scaling": args.scaling,
-                          "emulate_rank": args.emulate_rank or None}), file=line_out, flush=True)
+                          "emulate_rank": args.emulate_rank or None, "steps": args.steps, "warmup": args.warmup,
+                          "full": args.full, "dump_outputs": args.dump_outputs or None}), file=line_out, flush=True)
 
 
 def main():
@@ -407,9 +432,20 @@ def main():
     ap.add_argument("--python-steps", action="store_true",
                     help="one process: drive the timed steps from Python (one C-ABI call, one event wait, one native "
                          "reduction per step) instead of the native step loop")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: parity samples, extra blocks, CPU baselines, CMA-ES generation timing, "
+                         "roofline kernel timings, the collective by itself and the side file (a plain run times the "
+                         "headline steps only)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write what the last one computed: DIR/returns.npy (fp32 episode "
+                         "returns) and DIR/costs.npy (float64 per-candidate costs)")
     ap.add_argument("--plumbing-check", action="store_true", help=argparse.SUPPRESS)
     args = ap.parse_args()
     args.config = int(args.config) if args.config.isdigit() else args.config
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit(f"bench.py: --steps {args.steps} --warmup {args.warmup}: need steps >= 1, warmup >= 0")
+    if not args.full:                                       # a plain run: the headline and nothing else
+        args.no_extras = args.no_parity = args.no_cpu_baseline = True
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(spawn_ranks(args))
@@ -522,6 +558,7 @@ def main():
         rollout_fn, handle = eng.lib.ocd_rollout_episodes, eng._h
         init_ptr, w_ptr, stream_ptr = init_dev.data_ptr(), w_dev.data_ptr(), eng._stream()
         cost_buf = np.empty(hi - lo if not sharded else P, dtype=np.float64)
+        last = {"returns": host_np[:n_out]}                     # the returns array the last step reduced
 
         def generation():
             abi.check(eng.lib, rollout_fn(handle, init_ptr, w_ptr, P, N, e0, e1, out_ptr, None, None, stream_ptr))
@@ -537,6 +574,7 @@ def main():
                 arr = host_np
             else:                                                   # gloo rehearsal: gathered on the host already
                 arr = src.numpy()
+            last["returns"] = arr
             return sharding.fitness_from_returns(arr, P, N, S)
 
         # bring the GPU to its sustained clocks first (untimed; a cold process sees the same kernel take 1.73 ms and
@@ -575,22 +613,26 @@ def main():
             tt = torch.tensor([dt], dtype=torch.float64, device=device if args.backend == "nccl" else "cpu")
             dist.all_reduce(tt, op=dist.ReduceOp.MAX)
             dt = float(tt.item())
-        # dominant kernel: average launch duration from HIP events on the launch stream, writing where the timed
-        # generations write (one process: the pinned host buffer the kernel stores its returns into directly;
-        # sharded: the device buffer the all-gather reads) -- kernel_ms and ms_per_step describe the same launch
-        # (the MEDIAN of single-launch timings: one launch on a clock transition is +10 % and would move a mean over six)
-        kt = [eng.time_rollout(init_dev, w_dev, e0, e1, ret_dev if sharded else host[:n_out], reps=1)
-              for _ in range(max(7, min(steps, 21)))]
-        kern_ms = float(np.median(kt))
+        # what the last timed step handed its caller (copied before anything below reuses the buffers)
+        outputs = {"returns": np.array(last["returns"], dtype=np.float32),
+                   "costs": np.array(fit, dtype=np.float64)}
         launch = dict(eng.last_launch(), returns_written_to="device memory" if sharded else "pinned host memory (zero-copy)")
-        coll = None
-        if sharded:                                                # the generation's one collective by itself
-            coll = time_all_gather(ret_dev, P, N, S)
-        if sharded:                                                # every rank's kernel time, in rank order
-            got = [None] * dist.get_world_size()
-            dist.all_gather_object(got, float(kern_ms))
-            launch["kernel_ms_per_rank"] = got
-        return dt, kern_ms, fit, (cfg, scn, inits, w32, P, N, S, e1 - e0, launch, coll, eng, e0, sharded)
+        kern_ms, coll = None, None
+        if args.full:
+            # dominant kernel: average launch duration from HIP events on the launch stream, writing where the timed
+            # generations write (one process: the pinned host buffer the kernel stores its returns into directly;
+            # sharded: the device buffer the all-gather reads) -- kernel_ms and ms_per_step describe the same launch
+            # (the MEDIAN of single-launch timings: one launch on a clock transition is +10 % and would move a mean over six)
+            kt = [eng.time_rollout(init_dev, w_dev, e0, e1, ret_dev if sharded else host[:n_out], reps=1)
+                  for _ in range(max(7, min(steps, 21)))]
+            kern_ms = float(np.median(kt))
+            if sharded:                                            # the generation's one collective by itself
+                coll = time_all_gather(ret_dev, P, N, S)
+            if sharded:                                            # every rank's kernel time, in rank order
+                got = [None] * dist.get_world_size()
+                dist.all_gather_object(got, float(kern_ms))
+                launch["kernel_ms_per_rank"] = got
+        return dt, kern_ms, fit, (cfg, scn, inits, w32, P, N, S, e1 - e0, launch, coll, eng, e0, sharded, outputs)
 
     def parity_of(ctx):
         """The `parity` object of a block (None with --no-parity): this rank checks its own slice, counts are summed
@@ -852,18 +894,31 @@ def main():
         return out
 
     def block(cfg_index, dt, kern_ms, ctx, steps, per_gpu_only=False):
+        """The record of one timed workload; kern_ms None (a plain run: no kernel timing of its own) leaves out the
+        roofline and the counters."""
         cfg, scn, inits, w32, P, N, S, n_local, launch, _coll = ctx[:10]
+        n_done = n_local if per_gpu_only else P * N * S           # episodes this timing covers per step
+        d = scn.desc
+        n_split = max(1, round(P * N * S / max(n_local, 1)))
+        pop_text = (f"pop {P} split over {n_split} ranks" if n_split > 1 else f"pop {P}")
+        what = cfg["label"] if isinstance(cfg_index, str) else f"BASELINE config {cfg_index}"
+        out = {
+            "workload": f"{what}: {cfg['scenario']}, CMA-ES {pop_text} x {N} inits x "
+                        f"{S} samples, planning horizon H={d.horizon}, n_iter={d.n_iter}, K={d.n_ctrl_inits} control "
+                        f"inits, episode length T={d.episode_len}",
+            "episodes_per_generation": P * N * S, "episodes_per_gpu": n_local,
+            "value": n_done * steps / dt, "unit": "episodes/s", "ms_per_step": dt / steps * 1e3,
+        }
+        if kern_ms is None:
+            return out
         kernel_name = ("ocd::mpc_chunk_kernel" if launch["scan_mode"] == 4 else "ocd::mpc_kernel") + \
             f" ({launch['mapping']}" + (f", {launch['chunk']} steps per lane" if launch["chunk"] else "") + \
             f", {launch['trajectories_per_wavefront']} trajectories per wavefront, {launch['workgroups']} workgroups x " \
             f"{launch['wavefronts_per_workgroup']} wavefronts" + \
             (", latency build" if launch["build_wavefronts_per_simd"] == 1 else "") + ")"
-        n_done = n_local if per_gpu_only else P * N * S           # episodes this timing covers per step
-        d = scn.desc
         nbytes, flops = algorithmic_per_episode(d)
         ach_gbs = n_local * nbytes / (kern_ms * 1e-3) / 1e9
         ach_tf = n_local * flops / (kern_ms * 1e-3) / 1e12
-        n_split = max(1, round(P * N * S / max(n_local, 1)))
         from l4dc_mpc_ocd_amd import abi as _abi
         mangled = _abi.planner_kernel_name(d, launch)
         pmc, pmc_why = pmc_record(f"cfg{cfg_index}_share{n_split}" if per_gpu_only else
@@ -890,14 +945,7 @@ def main():
                 profiled["valu_issue_utilisation"] = pmc["sq_active_inst_valu"] / pmc["sq_wave_cycles"]
                 profiled["wait_fraction"] = pmc["sq_wait_any"] / pmc["sq_wave_cycles"]
                 profiled["valu_instructions_per_launch"] = pmc["sq_insts_valu"]
-        pop_text = (f"pop {P} split over {n_split} ranks" if n_split > 1 else f"pop {P}")
-        what = cfg["label"] if isinstance(cfg_index, str) else f"BASELINE config {cfg_index}"
-        out = {
-            "workload": f"{what}: {cfg['scenario']}, CMA-ES {pop_text} x {N} inits x "
-                        f"{S} samples, planning horizon H={d.horizon}, n_iter={d.n_iter}, K={d.n_ctrl_inits} control "
-                        f"inits, episode length T={d.episode_len}",
-            "episodes_per_generation": P * N * S, "episodes_per_gpu": n_local,
-            "value": n_done * steps / dt, "unit": "episodes/s", "ms_per_step": dt / steps * 1e3,
+        out.update({
             "roofline": {"bound": "hbm", "achieved": ach_gbs, "peak": HBM_PEAK_GBS, "unit": "GB/s",
                          "frac": ach_gbs / HBM_PEAK_GBS, "traffic": traffic,
                          "traffic_source": PMC_SOURCE if pmc else None,
@@ -911,7 +959,7 @@ def main():
                          "note": "the contract's hbm figures are kept as measured; the path is fp32-VALU issue bound, "
                                  "not HBM bound (SURVEY.md 8d): `binding` / `binding_frac` name the bound that binds"},
             "valu": valu,
-        }
+        })
         if profiled:
             out["profiled"] = profiled
         return out
@@ -934,6 +982,8 @@ def main():
             raise SystemExit(f"bench.py: population {P_total} < {world} ranks")
         dt, kern_ms, fit, ctx = timed_generations(args.config, P_total, world, rank, args.steps, args.warmup)
     coll = ctx[9]
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, ctx[13])
     head_parity = parity_of(ctx)
 
     # ---- extras: config 2 (small-batch latency) on rank 0, CMA-ES generation wall-clock on all ranks ----
@@ -1027,8 +1077,7 @@ def main():
                        "sharding": (f"rank {emulate[0]} of a {emulate[1]}-way strong split, emulated on one GPU (no collective)"
                                     if emulate else
                                     f"candidate blocks over {world} rank(s); one all_gather of fp32 returns per generation")},
-            "roofline": hb["roofline"],
-            "valu": hb["valu"],
+            **({"roofline": hb["roofline"], "valu": hb["valu"]} if args.full else {}),
             "generation_cost_checksum": float(np.sum(fit)),
         }
         if head_parity is not None:
@@ -1059,12 +1108,13 @@ def main():
             coll = {"error": f"{type(exc).__name__}: {exc}"[:300], "in_timed_step": False}
     elif coll is not None:
         coll["in_timed_step"] = True
-    if rank == 0:
+    if rank == 0 and args.full:
         out["collective"] = coll
         if world == 1 and "config4_whole" in shares and "config5_whole" in shares:
             g_us = coll["all_gather_us"] if coll and "all_gather_us" in coll else 0.0
             out["predicted_strong_scaling"] = predicted_strong_scaling({4: shares["config4_whole"], 5: shares["config5_whole"]}, g_us)
-        print_line(out, line_out)
+    if rank == 0:
+        print_line(out, line_out, detail=args.full)
     if dist.is_initialized():
         dist.destroy_process_group()
 

@@ -10,7 +10,7 @@
  * Why not libm: the reference computes tf.exp / tf.sin / tf.cos through
  * TensorFlow 2.1.0's Eigen kernels (interact_drive/math_utils.py:30,177,
  * interact_drive/simulation_utils.py:16-17, experiments/merging.py:52).  Their
- * ulp-level behaviour is not under /root/reference (third-party, pinned in
+ * ulp-level behaviour is not in the reference repository (third-party, pinned in
  * requirements.txt:69-71) and differs from glibc and from AMD's ocml, so no
  * choice reproduces TensorFlow bit-for-bit.  What CAN be guaranteed is
  * oracle == kernel, and that needs one algorithm written down operation by

@@ -55,3 +55,18 @@ def test_strong_scaling_and_rank_emulation_flags():
     # one rank's block is emulated on ONE GPU: not together with several ranks
     r = run(["--gpus", "2", "--emulate-rank", "0/8", "--plumbing-check"], env_extra={"WORLD_SIZE": "2", "RANK": "0", "LOCAL_RANK": "0"})
     assert r.returncode != 0 and "one GPU" in (r.stderr + r.stdout)
+
+
+def test_full_and_dump_flags_and_step_counts():
+    # a plain run unless --full; --dump-outputs names a directory; --steps / --warmup are taken as given
+    r = run(["--gpus", "1", "--plumbing-check", "--steps", "7", "--warmup", "3"])
+    assert r.returncode == 0, r.stderr[-2000:]
+    rec = last_json(r.stdout)
+    assert rec["full"] is False and rec["dump_outputs"] is None and rec["steps"] == 7 and rec["warmup"] == 3
+    r = run(["--gpus", "1", "--plumbing-check", "--full", "--dump-outputs", "out_dir"])
+    assert r.returncode == 0, r.stderr[-2000:]
+    rec = last_json(r.stdout)
+    assert rec["full"] is True and rec["dump_outputs"] == "out_dir"
+    for bad in (["--steps", "0"], ["--warmup", "-1"]):
+        r = run(["--gpus", "1", "--plumbing-check"] + bad)
+        assert r.returncode != 0 and "--steps" in (r.stderr + r.stdout)

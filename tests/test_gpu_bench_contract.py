@@ -1,10 +1,12 @@
 """bench.py on a real GPU: one JSON line with the contract's keys, the roofline / cpu_baseline objects,
-and numbers that are consistent with each other."""
+and numbers that are consistent with each other (--full); a plain run times the headline alone and dumps what its last
+step computed."""
 import json
 import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -12,7 +14,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def test_bench_json_line():
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "6", "--warmup", "2"],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "6", "--warmup", "2"],
                        capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-3000:]
     # stdout is the JSON line and nothing else: what libraries print to file descriptor 1 (RCCL's version banner when the
@@ -32,6 +34,44 @@ def test_bench_json_line():
     assert line["roofline"]["kernel_ms"] == d["roofline"]["kernel_ms"] and line["roofline"]["frac"] == d["roofline"]["frac"]
     assert line["cpu_baseline"]["value"] == d["cpu_baseline"]["value"]
     check_detail(d)
+
+
+def test_plain_run_times_the_headline_and_dumps_its_outputs(tmp_path):
+    """Without --full: the contract's keys and nothing measured beside the headline (no parity, roofline, CPU figure,
+    collective or side file); --dump-outputs writes the last timed step's episode returns and per-candidate costs, and
+    they are the CPU oracle's on the seeded inputs of BASELINE config 3."""
+    env = dict(os.environ, OCD_BENCH_DETAIL=str(tmp_path / "detail.json"))
+    out_dir = tmp_path / "outputs"
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "5", "--warmup", "1",
+                        "--dump-outputs", str(out_dir)], capture_output=True, text=True, timeout=600, env=env)
+    assert r.returncode == 0, r.stderr[-3000:]
+    assert r.stdout.count("\n") == 1 and r.stdout.startswith("{"), r.stdout[:400]
+    line = json.loads(r.stdout)
+    for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
+              "vs_baseline", "dtype", "data", "config", "generation_cost_checksum"):
+        assert k in line, k
+    assert line["steps"] == 5 and line["warmup"] == 1 and line["n_gpus"] == 1 and line["dtype"] == "f32"
+    assert line["unit"] == "episodes/s" and line["higher_is_better"] is True and line["metric"].startswith("MPC episode rollouts/sec at H=10")
+    assert line["config"]["episodes_per_generation"] == 2048
+    assert abs(line["value"] - 2048 / (line["ms_per_step"] * 1e-3)) / line["value"] < 1e-6
+    for k in ("roofline", "parity", "cpu_baseline", "collective", "cma_generation_ms", "config2", "predicted_strong_scaling",
+              "detail"):
+        assert k not in line, k
+    assert not (tmp_path / "detail.json").exists()
+    returns, costs = np.load(out_dir / "returns.npy"), np.load(out_dir / "costs.npy")
+    assert sorted(os.listdir(out_dir)) == ["costs.npy", "returns.npy"]
+    assert returns.dtype == np.float32 and returns.shape == (2048,) and costs.dtype == np.float64 and costs.shape == (64,)
+    from l4dc_mpc_ocd_amd import scenarios, sharding
+    assert np.array_equal(costs, sharding.fitness_from_returns(returns, 64, 32, 1))
+    assert float(np.sum(costs)) == line["generation_cost_checksum"]
+    # the inputs bench.py seeds for config 3 (workload(): inits from seed 1003, candidates from seed 2003)
+    cfg = scenarios.BASELINE_CONFIGS[3]
+    scn = scenarios.SCENARIOS[cfg["scenario"]](horizon=cfg["horizon"])
+    inits = scn.init_dist.sample(cfg["n_inits"], seed=1003)
+    w32 = np.stack([scenarios.planner_weights_fp32(c) for c in scn.candidate_weights(cfg["pop"], seed=2003)])
+    import oracle_lib
+    ref = oracle_lib.load().rollout(scn.desc, inits, w32)["returns"]
+    assert np.array_equal(returns.view(np.uint32), np.asarray(ref, dtype=np.float32).view(np.uint32))
 
 
 TIMING = bool(os.environ.get("OCD_TIMING_ASSERTS"))     # absolute wall-clock thresholds of the builder's box: opt-in

@@ -17,13 +17,13 @@ BENCH = os.path.join(ROOT, "bench.py")
 
 
 def run(args, timeout=600):
-    """One bench.py run: the printed line stays under its cap (N > 1 too), and the FULL record -- the side file the line
-    names -- is what the assertions below read."""
+    """One bench.py --full run: the printed line stays under its cap (N > 1 too), and the FULL record -- the side file
+    the line names -- is what the assertions below read."""
     import tempfile
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     with tempfile.TemporaryDirectory() as tmp:
         env["OCD_BENCH_DETAIL"] = os.path.join(tmp, "detail.json")
-        r = subprocess.run([sys.executable, BENCH] + args, capture_output=True, text=True, env=env, timeout=timeout)
+        r = subprocess.run([sys.executable, BENCH, "--full"] + args, capture_output=True, text=True, env=env, timeout=timeout)
         assert r.returncode == 0, (r.stdout[-1000:], r.stderr[-3000:])
         lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
         assert len(lines) == 1 and len(lines[0]) < 8192, r.stdout[-2000:]
@@ -116,3 +116,26 @@ def test_two_ranks_carry_baseline_configs_4_and_5_with_parity():
         one = run(["--gpus", "1", "--config", str(c), "--scaling", "strong", "--no-parity"] + COMMON)
         assert one["config"]["episodes_per_generation"] == blk["episodes_per_generation"]
         assert one["generation_cost_checksum"] == blk["generation_cost_checksum"], c
+
+
+def test_plain_two_ranks_dump_what_one_rank_dumps(tmp_path):
+    """Without --full (the headline alone): two gloo ranks under strong scaling hand back, in their last timed step, the
+    same episode returns and candidate costs as one rank does with the whole population."""
+    import numpy as np
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
+    got = {}
+    port = 30100 + os.getpid() % 200
+    for n, extra in ((1, []), (2, ["--backend", "gloo", "--master-port", str(port)])):
+        out = tmp_path / f"n{n}"
+        r = subprocess.run([sys.executable, BENCH, "--gpus", str(n), "--scaling", "strong", "--steps", "3", "--warmup", "1",
+                            "--dump-outputs", str(out)] + extra, capture_output=True, text=True, env=env, timeout=600)
+        assert r.returncode == 0, (r.stdout[-1000:], r.stderr[-3000:])
+        lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+        assert len(lines) == 1, r.stdout[-2000:]
+        line = json.loads(lines[0])
+        assert line["n_gpus"] == n and line["steps"] == 3 and "parity" not in line and "roofline" not in line
+        got[n] = (line, np.load(out / "returns.npy"), np.load(out / "costs.npy"))
+    assert got[1][1].shape == got[2][1].shape == (2048,) and got[1][2].shape == got[2][2].shape == (64,)
+    assert np.array_equal(got[1][1].view(np.uint32), got[2][1].view(np.uint32))
+    assert np.array_equal(got[1][2], got[2][2])
+    assert got[1][0]["generation_cost_checksum"] == got[2][0]["generation_cost_checksum"] == float(np.sum(got[1][2]))

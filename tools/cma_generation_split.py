@@ -1,5 +1,5 @@
-import sys, numpy as np
-sys.path.insert(0,'/root/repo')
+import os, sys, numpy as np
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from l4dc_mpc_ocd_amd import scenarios
 from l4dc_mpc_ocd_amd.interact_drive.experiments import run_mpc_ord as rmo
 cfg = scenarios.BASELINE_CONFIGS[3]

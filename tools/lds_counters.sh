@@ -6,7 +6,7 @@ OUT="$ROOT/gpurun_out/lds_prof"
 mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp
 for c in 4 5; do
-  rocprofv3 --pmc SQ_INSTS_LDS SQ_LDS_BANK_CONFLICT SQ_LDS_ADDR_CONFLICT SQ_LDS_IDX_ACTIVE SQ_ACTIVE_INST_LDS SQ_WAVE_CYCLES --kernel-trace -d "$OUT/c$c" -o res -- python3 "$ROOT"/bench.py --config $c --steps 4 --warmup 1 --no-extras --no-cpu-baseline --no-parity > "$OUT/c$c.log" 2>&1
+  rocprofv3 --pmc SQ_INSTS_LDS SQ_LDS_BANK_CONFLICT SQ_LDS_ADDR_CONFLICT SQ_LDS_IDX_ACTIVE SQ_ACTIVE_INST_LDS SQ_WAVE_CYCLES --kernel-trace -d "$OUT/c$c" -o res -- python3 "$ROOT"/bench.py --full --config $c --steps 4 --warmup 1 --no-extras --no-cpu-baseline --no-parity > "$OUT/c$c.log" 2>&1
 done
 cd "$ROOT"
 python3 - "$OUT" <<'PY' > "$ROOT/gpurun_out/lds_counters.txt"

@@ -43,7 +43,7 @@ def counters_json(round_name, out_dir):
     import os
     import re
     rec = {"_source": f"profiles/{round_name}_cfg<N>_rocprofv3.txt: rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE / SQ_* "
-                      "(separate passes, --kernel-trace only) of `bench.py --config N [--emulate-rank 0/8] --no-extras`, kernels ocd::mpc_kernel / ocd::mpc_chunk_kernel (cfgN_share8: rank 0's block of an 8-way split); "
+                      "(separate passes, --kernel-trace only) of `bench.py --full --config N [--emulate-rank 0/8] --no-extras`, kernels ocd::mpc_kernel / ocd::mpc_chunk_kernel (cfgN_share8: rank 0's block of an 8-way split); "
                       "FETCH/WRITE in KiB per launch as counted (dword-granular accesses), SQ_* per launch (quad-cycles)"}
     # which tree the profiled kernels were built from: the commit (given by the caller: the GPU box holds no .git) and
     # the hash of the kernel sources, which bench.py recomputes before it replays any of these numbers
